@@ -2,11 +2,18 @@
 on MI355X, one process per GPU, sessions sharded across GPUs with no collective.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--config north|1|3] [--frames F] [--payload P]
+                  [--full] [--dump-outputs DIR]
 
 A step = one pass of the decode pipeline (libwsgpu's HIP kernels) over one batch
 of F synthetic masked frames per GPU resident in HBM.  Default workload: the
 north-star 1-GPU case, 1 M x 4 KiB masked TEXT frames (valid UTF-8, ~70 % ASCII
 bytes) in 1024 sessions, validation on.  Prints ONE JSON line (rank 0).
+
+A plain run sets up, warms up, times the K steps and prints the headline line.
+--full adds every other measurement to that line: the per-kernel breakdown, the
+copy ceiling, the validator stage, the host->device->host lines, the secondary
+BASELINE configs and the CPU baselines.  --dump-outputs DIR writes the last timed
+step's outputs as .npy files, the same from run to run with the same arguments.
 
 --gpus N > 1 without a torch.distributed environment starts N rank processes
 itself (torch.distributed.run, 127.0.0.1) before anything touches a GPU and
@@ -74,6 +81,13 @@ def parse():
     ap.add_argument("--sessions", type=int, default=None, help="sessions per GPU")
     ap.add_argument("--binary", action="store_true", help="BINARY frames (unmask only, no UTF-8 work)")
     ap.add_argument("--no-validate", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure everything beside the headline: the per-kernel "
+                         "breakdown, the copy ceiling, the validator stage, the host->device->host lines, the "
+                         "secondary configs and the CPU baselines (the options below that trim them apply here)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step's decode left in the caller's buffers as DIR/<name>.npy "
+                         "(dump_outputs)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
     ap.add_argument("--pmc-json", default=os.path.join(ROOT, "profiles", "pmc_traffic.json"))
@@ -323,23 +337,27 @@ def main():
     ctx.set_timing(False)
     ctx.set_timing_every(1)
     timing = ctx.timing()
-    pipe = pipeline_breakdown(ctx, step, dev)
+    if args.dump_outputs:  # (before any further step() and before copy_ceiling: both overwrite the buffers)
+        dump_outputs(args.dump_outputs if world == 1 else os.path.join(args.dump_outputs, f"rank{rank}"),
+                     payload, desc, res, state, F)
+    full = args.full  # everything beside the headline figure
+    pipe = pipeline_breakdown(ctx, step, dev) if full else None
     validator = None  # (before copy_ceiling, which overwrites the payload buffer)
-    if world == 1 and not args.no_extras and not args.binary:
+    if full and world == 1 and not args.no_extras and not args.binary:
         validator = validator_line(ctx, dev, desc, sf, payload, n_s, F, P, args.extra_steps)
 
     # dominant kernel: k_piecesN reads each frame's payload bytes off the wire and writes them unmasked
     unmask_ms, unmask_n = timing["k_piecesN"]
     avg_unmask_s = unmask_ms / 1e3 / max(1, unmask_n)
     alg_bytes = wire_bytes + F * P  # per launch: wire read + payload written
-    copy = benchsupport.copy_ceiling(ctx, wire, payload, wire_bytes)
+    copy = benchsupport.copy_ceiling(ctx, wire, payload, wire_bytes) if full else None
     achieved = alg_bytes / avg_unmask_s / 1e9
     # HBM bytes per launch from the PMC counters: PMC cannot run in the same process as
     # the timed region (separate rocprofv3 --pmc passes, MI355X_MICROARCH.md), so this is
     # the committed measurement of the same kernel on the same workload, labelled with
     # its file (traffic_source); null when none exists for this workload
     traffic = traffic_source = None
-    if os.path.exists(args.pmc_json):
+    if full and os.path.exists(args.pmc_json):
         try:
             with open(args.pmc_json) as fh:
                 pmc = json.load(fh)
@@ -352,11 +370,11 @@ def main():
             traffic = traffic_source = None
 
     e2e = None
-    if (args.e2e or (world == 1 and not args.no_extras)) and not args.no_e2e:
+    if full and (args.e2e or (world == 1 and not args.no_extras)) and not args.no_e2e:
         e2e = e2e_rate(ctx, cfg, wire, off, sf, n_s, wire_bytes, F, dev)
 
     extras = None
-    if world == 1 and not args.no_extras:
+    if full and world == 1 and not args.no_extras:
         del wire, payload, desc, res, state, off, sf
         torch.cuda.empty_cache()
         # the pinned buffers of the lines above (≈ 13 GB, held by torch's pinned-memory
@@ -386,7 +404,7 @@ def main():
     # the CPU baseline runs after every timed region, on rank 0 only (at N > 1 the
     # other ranks wait for it at the closing barrier)
     cpu = cpu_mt = None
-    if rank == 0 and not args.no_cpu_baseline:
+    if full and rank == 0 and not args.no_cpu_baseline:
         cpu = cpu_baseline(args, args.cpu_seconds)
         cpu_mt = cpu_baseline_mt(args, 5.0)
 
@@ -431,23 +449,24 @@ def main():
                 "alg_bytes_per_launch": alg_bytes,
                 "avg_launch_ms": round(avg_unmask_s * 1e3, 4),
                 "launches_timed": int(unmask_n), "event_every": EVENT_EVERY[0],
-                "copy_ceiling_GBs": round(copy, 1),
-                "frac_of_copy_ceiling": round(achieved / copy, 4),
                 # the north star's "HBM read-bandwidth fraction": wire bytes read / time / 8 TB/s,
                 # over the streaming kernel and over the whole step
                 "read_frac": round(wire_bytes / avg_unmask_s / 1e9 / HBM_PEAK_GBS, 4),
                 "read_frac_step": round(wire_bytes / (ms_step / 1e3) / 1e9 / HBM_PEAK_GBS, 4),
             },
-            "pipeline_ms": pipe,
-            "cpu_baseline": cpu,
-            "cpu_baseline_threads": cpu_mt,
+            "full": full,
         }
+        if full:
+            out["roofline"].update({"copy_ceiling_GBs": round(copy, 1),
+                                    "frac_of_copy_ceiling": round(achieved / copy, 4)})
+            out.update({"pipeline_ms": pipe, "cpu_baseline": cpu, "cpu_baseline_threads": cpu_mt})
         # NOT measured by this run: the same kernel's mean launch in the committed rocprofv3
         # profile of this workload (another process, maybe another build or box), kept
         # apart from the measured roofline block as a cross-reference
-        prof_ms, prof_src = profiled_launch("north" if args.config == "north" and not args.binary else
-                                            {"1": "configs1", "3": "configs3"}.get(args.config, "north"),
-                                            "k_piecesN<1, 1, 2")  # (rocprof prints the defaulted template arguments too)
+        prof_ms, prof_src = (None, None) if not full else \
+            profiled_launch("north" if args.config == "north" and not args.binary else
+                            {"1": "configs1", "3": "configs3"}.get(args.config, "north"),
+                            "k_piecesN<1, 1, 2")  # (rocprof prints the defaulted template arguments too)
         if prof_ms and F == 1 << 20 and P == 4096 and not args.binary:
             pf = alg_bytes / (prof_ms / 1e3) / 1e9 / HBM_PEAK_GBS
             out["reference_profile"] = {"source": prof_src, "launch_ms": round(prof_ms, 4), "frac": round(pf, 4),
@@ -463,6 +482,53 @@ def main():
     if dist:
         dist.barrier()  # (the other ranks wait here for rank 0's CPU baseline)
         dist.destroy_process_group()
+
+
+DUMP_FRAMES = 1 << 20         # descriptors dumped (all of them up to this many frames)
+DUMP_PAYLOAD_FRAMES = 1024    # frames whose payload bytes are dumped
+DUMP_PAYLOAD_BYTES = 8 << 20  # ... and at most this many bytes of them
+
+
+def dump_outputs(dirname, payload, desc, res, state, F):
+    """--dump-outputs: what decode_device left in the caller's buffers after the last timed
+    step, as float .npy files (every value is an integer a float64 / float32 holds exactly):
+      frames.npy           the frames whose descriptors are dumped: all up to DUMP_FRAMES, a
+                           fixed seeded sample of a larger batch
+      desc_<field>.npy     FrameDesc fields of those frames
+      result_<field>.npy   SessionResult fields of every session
+      state.npy            SessionState bytes of every session, [sessions, 8]
+      payload_frames.npy   the frames whose payloads are dumped (a fixed seeded sample)
+      payload_bytes.npy    their unmasked payload bytes, concatenated in that order
+    About 55 MB at the default workload.  Samples depend on F alone."""
+    import numpy as np
+    import torch
+    from snf4j_amd._lib import DESC_DTYPE, RESULT_DTYPE
+    os.makedirs(dirname, exist_ok=True)
+
+    def save(name, a, dt):
+        np.save(os.path.join(dirname, name + ".npy"), np.ascontiguousarray(a, dtype=dt))
+
+    rng = np.random.default_rng(0xD0C5)
+    frames = np.arange(F) if F <= DUMP_FRAMES else np.sort(rng.choice(F, DUMP_FRAMES, replace=False))
+    d = desc.cpu().numpy().view(DESC_DTYPE)[frames]
+    save("frames", frames, np.float64)
+    for name in ("payload_off", "payload_len"):
+        save("desc_" + name, d[name], np.float64)
+    for name in ("opcode", "flags", "status"):
+        save("desc_" + name, d[name], np.float32)
+    r = res.cpu().numpy().view(RESULT_DTYPE)
+    for name in RESULT_DTYPE.names:
+        save("result_" + name, r[name], np.float64)
+    save("state", state.cpu().numpy().reshape(-1, 8), np.float32)
+    pick = np.sort(rng.choice(len(frames), min(len(frames), DUMP_PAYLOAD_FRAMES), replace=False))
+    lens = d["payload_len"][pick].astype(np.int64)
+    pick = pick[np.cumsum(lens) <= DUMP_PAYLOAD_BYTES]
+    offs, lens = d["payload_off"][pick].astype(np.int64), d["payload_len"][pick].astype(np.int64)
+    # gather the picked frames' byte ranges on the device: one index per dumped byte
+    start = np.repeat(offs - (np.cumsum(lens) - lens), lens) + np.arange(int(lens.sum()))
+    got = payload[torch.from_numpy(start).to(payload.device)].cpu().numpy()
+    save("payload_frames", frames[pick], np.float64)
+    save("payload_bytes", got, np.float32)
 
 
 def profiled_launch(line: str, kernel_prefix: str):

@@ -16,8 +16,8 @@ step() {  # step <name> <seconds> <cmd...>
 step pytest_gpu 900 python -u -m pytest tests -m gpu -x -v -p no:cacheprovider --timeout 300 --timeout-method thread || exit $?
 step smoke 300 python -c "import __graft_entry__ as g; g.smoke()" || exit $?
 # N=2 through bench.py's own launcher, both ranks on device 0 (a rehearsal, not a number)
-WSG_BENCH_ONE_DEVICE=1 step bench_n2_rehearsal 300 python bench.py --gpus 2 --frames 262144 --steps 5 --warmup 2 --cpu-seconds 2 || exit $?
-step bench_config3 300 python bench.py --config 3 --steps 5 --warmup 2 --no-extras --no-cpu-baseline || exit $?
+WSG_BENCH_ONE_DEVICE=1 step bench_n2_rehearsal 300 python bench.py --full --gpus 2 --frames 262144 --steps 5 --warmup 2 --cpu-seconds 2 || exit $?
+step bench_config3 300 python bench.py --full --config 3 --steps 5 --warmup 2 --no-extras --no-cpu-baseline || exit $?
 [ "$1" = quick ] && { echo ALL_DONE; exit 0; }
-step bench 600 python bench.py --e2e || exit $?
+step bench 600 python bench.py --full --e2e || exit $?
 echo ALL_DONE
