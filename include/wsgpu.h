@@ -809,6 +809,16 @@ typedef enum wsg_hs_cause {
     WSG_HSC_MISSING_SUBPROTOCOL = 21,   /* "Missing websocket sub protocol" :476 */
     WSG_HSC_INVALID_SUBPROTOCOL = 22,   /* "Invalid websocket sub protocol: %s" :483 */
     WSG_HSC_INVALID_EXTENSIONS = 23,    /* validateExtensions false with no reason set (:529-532): null */
+    /* negotiation (wsg_handshake_*_negotiate_batch_*) */
+    WSG_HSC_INVALID_REQUEST_EXTENSION = 24, /* "Invalid websocket request extension" Handshaker.java:321 (400) */
+    /* "Invalid extension: " + InvalidExtensionException.getMessage() (:506), the six texts of
+       PerMessageDeflateParams.set/setInt/parse (PerMessageDeflateParams.java:85-145) */
+    WSG_HSC_EXT_DUPLICATED = 25,        /* "Invalid extension: Duplicated parameter" */
+    WSG_HSC_EXT_UNNECESSARY_VALUE = 26, /* "Invalid extension: Unnecessary parameter value" */
+    WSG_HSC_EXT_MISSING_VALUE = 27,     /* "Invalid extension: Missing parameter value" */
+    WSG_HSC_EXT_VALUE_FORMAT = 28,      /* "Invalid extension: Invalid parameter value format" */
+    WSG_HSC_EXT_VALUE = 29,             /* "Invalid extension: Invalid parameter value" */
+    WSG_HSC_EXT_UNEXPECTED = 30,        /* "Invalid extension: Unexpected parameter" */
     /* why a request was deferred (WSG_HS_DEFER) */
     WSG_HSC_D_LINE_FORM = 32, WSG_HSC_D_REPEATED = 33, WSG_HSC_D_NON_ASCII = 34, WSG_HSC_D_URI = 35,
     WSG_HSC_D_HOST = 36, WSG_HSC_D_SUBPROTOCOL = 37, WSG_HSC_D_EXTENSION = 38, WSG_HSC_D_POLICY = 39,
@@ -866,6 +876,100 @@ int wsg_handshake_validate_batch_device(wsg_ctx* ctx, const wsg_hs_config* cfg, 
 int wsg_handshake_validate_batch_host(wsg_ctx* ctx, const wsg_hs_config* cfg, const uint8_t* resp,
                                       const uint64_t* resp_off, const uint8_t* keys, uint32_t n,
                                       uint8_t* expected_out, wsg_hs_result* result);
+
+/* ---------------- opening handshake with negotiation on the device ---------------- */
+/* A second pair of entry points that decide what the pair above defers when the config
+ * lists subprotocols or extensions, for the one extension this library implements:
+ *   Handshaker.acceptSubProtocol / acceptExtensions       Handshaker.java:259-325
+ *   Handshaker.validateSubProtocol / validateExtensions   Handshaker.java:462-533
+ *   HandshakeUtils.extension (both directions)            HandshakeUtils.java:195-247
+ *   PerMessageDeflateParams.parse                         PerMessageDeflateParams.java:83-154
+ *   PerMessageDeflateExtension.acceptOffer / validateResponse / response
+ *                                                         PerMessageDeflateExtension.java:177-301
+ * The semantics are the reference's, byte for byte, where they differ from RFC 7692 too
+ * (every offer named permessage-deflate is parsed, also after one was accepted; a
+ * client_max_window_bits without a value declines a server's answer).
+ *
+ * Server side (after acceptKey): the first requested subprotocol token, in request order,
+ * that equals a supported entry ("*" matches any token) is answered; the first offer
+ * acceptOffer does not decline is accepted; an InvalidExtensionException in any offer is
+ * 400 / WSG_HSC_INVALID_REQUEST_EXTENSION.  The 101 response gains, after
+ * Sec-WebSocket-Accept, "Sec-WebSocket-Protocol: <token>" and "Sec-WebSocket-Extensions:
+ * permessage-deflate[; client_no_context_takeover][; server_no_context_takeover]".
+ * Client side (after validateKeyChallenge): the whole Sec-WebSocket-Protocol value must
+ * equal one supported entry ("*" is no wildcard there); every element of
+ * Sec-WebSocket-Extensions must be a permessage-deflate answer validateResponse takes, and
+ * only one of them (else WSG_HSC_INVALID_EXTENSIONS, or WSG_HSC_EXT_* when the parameters
+ * throw).
+ *
+ * Still deferred (WSG_HS_DEFER): every form the pair above defers for other reasons; an
+ * extensions field when other_extensions is set (WSG_HSC_D_EXTENSION); a chosen
+ * subprotocol token longer than WSG_HS_NEG_MAX_TOKEN (WSG_HSC_D_SUBPROTOCOL).
+ * cfg->subprotocols and cfg->extensions are not read by these entry points: the
+ * negotiation struct says what is configured. */
+#define WSG_HS_NEG_MAX_PROTOCOLS 16        /* supported subprotocols at most */
+#define WSG_HS_NEG_MAX_PROTOCOL_BYTES 256  /* their bytes in all at most */
+#define WSG_HS_NEG_RESP_STRIDE 384   /* response bytes reserved per request: 129 (the plain 101) + 26 + token
+                                        (Sec-WebSocket-Protocol) + 102 (Sec-WebSocket-Extensions) */
+#define WSG_HS_NEG_MAX_TOKEN 96      /* the longest subprotocol token the response slot is sized for */
+
+#define WSG_HS_NOCONTEXT_FORBIDDEN 0 /* PerMessageDeflateExtension.NoContext */
+#define WSG_HS_NOCONTEXT_OPTIONAL 1
+#define WSG_HS_NOCONTEXT_REQUIRED 2
+
+typedef struct wsg_hs_negotiation {
+    uint8_t n_protocols;            /* getSupportedSubProtocols(): entries (0: none configured) */
+    uint8_t deflate;                /* getSupportedExtensions() holds one PerMessageDeflateExtension */
+    uint8_t other_extensions;       /* ... or anything else: an extensions field is deferred */
+    uint8_t compress_no_context;    /* that extension's compressNoContext (WSG_HS_NOCONTEXT_*) */
+    uint8_t decompress_no_context;  /* ... and decompressNoContext */
+    uint8_t reserved[3];
+    uint16_t protocol_off[WSG_HS_NEG_MAX_PROTOCOLS + 1]; /* entry k is protocol_bytes[protocol_off[k],
+                                       protocol_off[k+1]); protocol_off[0] = 0, ascending */
+    uint8_t reserved2[6];
+    uint8_t protocol_bytes[WSG_HS_NEG_MAX_PROTOCOL_BYTES];
+} wsg_hs_negotiation; /* 304 bytes */
+
+#define WSG_HS_EXT_DEFLATE 0x01            /* permessage-deflate was negotiated */
+#define WSG_HS_EXT_CLIENT_NO_CONTEXT 0x02  /* PerMessageDeflateParams.isClientNoContext() */
+#define WSG_HS_EXT_SERVER_NO_CONTEXT 0x04  /* ... isServerNoContext() */
+
+/* What a switched session negotiated: all zero unless kind is ACCEPT with status 101, or
+ * FINISHED.  The server's encoder runs with SERVER_NO_CONTEXT and its decoder with
+ * CLIENT_NO_CONTEXT, the client's the other way round
+ * (PerMessageDeflateExtension.java:310,323). */
+typedef struct wsg_hs_negotiated {
+    uint32_t proto_off;   /* the subprotocol: bytes [proto_off, +proto_len) of the request */
+    uint16_t proto_len;   /*   (server) or of the response (client); 0: none */
+    uint8_t ext;          /* WSG_HS_EXT_* */
+    uint8_t reserved;
+} wsg_hs_negotiated; /* 8 bytes */
+
+/* wsg_handshake_accept_batch_* with the negotiation decided on the device: the same
+ * arguments, `neg` (a host pointer for both variants; it travels as a kernel argument) and
+ * negotiated[n] (8-B aligned).  Responses are written to resp[i * WSG_HS_NEG_RESP_STRIDE,
+ * + resp_len).  WSG_API_EINVAL for a malformed `neg`: more than WSG_HS_NEG_MAX_PROTOCOLS
+ * entries, protocol_off not starting at 0, descending or past
+ * WSG_HS_NEG_MAX_PROTOCOL_BYTES, a flag above 1, a NoContext value above 2. */
+int wsg_handshake_accept_negotiate_batch_device(wsg_ctx* ctx, const wsg_hs_config* cfg,
+                                                const wsg_hs_negotiation* neg, const uint8_t* req,
+                                                const uint64_t* req_off, uint32_t n, uint8_t* resp,
+                                                wsg_hs_result* result, wsg_hs_negotiated* negotiated);
+int wsg_handshake_accept_negotiate_batch_host(wsg_ctx* ctx, const wsg_hs_config* cfg,
+                                              const wsg_hs_negotiation* neg, const uint8_t* req,
+                                              const uint64_t* req_off, uint32_t n, uint8_t* resp,
+                                              wsg_hs_result* result, wsg_hs_negotiated* negotiated);
+/* wsg_handshake_validate_batch_* likewise. */
+int wsg_handshake_validate_negotiate_batch_device(wsg_ctx* ctx, const wsg_hs_config* cfg,
+                                                  const wsg_hs_negotiation* neg, const uint8_t* resp,
+                                                  const uint64_t* resp_off, const uint8_t* keys, uint32_t n,
+                                                  uint8_t* expected_out, wsg_hs_result* result,
+                                                  wsg_hs_negotiated* negotiated);
+int wsg_handshake_validate_negotiate_batch_host(wsg_ctx* ctx, const wsg_hs_config* cfg,
+                                                const wsg_hs_negotiation* neg, const uint8_t* resp,
+                                                const uint64_t* resp_off, const uint8_t* keys, uint32_t n,
+                                                uint8_t* expected_out, wsg_hs_result* result,
+                                                wsg_hs_negotiated* negotiated);
 
 #ifdef __cplusplus
 }

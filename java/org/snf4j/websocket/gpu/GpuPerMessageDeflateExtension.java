@@ -14,9 +14,14 @@
  * compression level; behind a GpuFrameEncoder it compresses in that encoder's device
  * batch.  The level: the one given here (PerMessageDeflateExtension keeps its own
  * private), 6 by default as PerMessageDeflateExtension() (:144-146).
+ *
+ * GpuHandshakeNegotiator (below) carries the same extension's settings to the
+ * handshake natives that negotiate on the device.
  */
 package org.snf4j.websocket.gpu;
 
+import java.nio.ByteBuffer;
+import java.nio.charset.StandardCharsets;
 import java.util.List;
 
 import org.snf4j.core.codec.ICodec;
@@ -130,5 +135,76 @@ public class GpuPerMessageDeflateExtension implements IExtension {
 					PerMessageDeflateExtension.PERMESSAGE_DEFLATE_DECODER,
 					new GpuPerMessageDeflateDecoder(noContext, (PerMessageDeflateDecoder) c));
 		}
+	}
+}
+
+/**
+ * The settings of the negotiating handshake natives (wsg_hs_negotiation): the config's
+ * supported subprotocols and the two NoContext values of its one
+ * PerMessageDeflateExtension.  PerMessageDeflateExtension keeps compressNoContext and
+ * decompressNoContext private, so they are given here and not read from a delegate
+ * (as the compression level above).  deflate == false: no extension is supported;
+ * otherExtensions: the supported list holds anything else, and an extensions field is
+ * deferred to the Java Handshaker as before.
+ */
+final class GpuHandshakeNegotiator {
+
+	private final byte[] image;
+
+	GpuHandshakeNegotiator(String[] subProtocols, boolean deflate, NoContext compressNoContext,
+			NoContext decompressNoContext, boolean otherExtensions) {
+		image = pack(subProtocols, deflate, compressNoContext, decompressNoContext, otherExtensions);
+	}
+
+	/** false: the lists exceed the native caps; the caller sets the config's flags and offers are deferred */
+	boolean fits() {
+		return image != null;
+	}
+
+	/**
+	 * The little-endian image of wsg_hs_negotiation: n_protocols, deflate, other_extensions,
+	 * compress_no_context, decompress_no_context, 3 reserved bytes; protocol_off[17] (u16) at 8;
+	 * protocol_bytes[256] at 48.  null when the subprotocols do not fit (16 entries, 256
+	 * bytes, ASCII).
+	 */
+	static byte[] pack(String[] subProtocols, boolean deflate, NoContext compressNoContext,
+			NoContext decompressNoContext, boolean otherExtensions) {
+		int n = subProtocols == null ? 0 : subProtocols.length;
+		if (n > Wsg.HS_NEG_MAX_PROTOCOLS)
+			return null;
+		byte[] b = new byte[Wsg.HS_NEGOTIATION_BYTES];
+		b[0] = (byte) n;
+		b[1] = (byte) (deflate ? 1 : 0);
+		b[2] = (byte) (otherExtensions ? 1 : 0);
+		b[3] = (byte) (deflate ? compressNoContext.ordinal() : 0); // FORBIDDEN, OPTIONAL, REQUIRED = 0, 1, 2
+		b[4] = (byte) (deflate ? decompressNoContext.ordinal() : 0);
+		int at = 0;
+		for (int k = 0; k < n; ++k) {
+			String s = subProtocols[k];
+			for (int i = 0; i < s.length(); ++i)
+				if (s.charAt(i) > 0x7f)
+					return null;
+			byte[] p = s.getBytes(StandardCharsets.US_ASCII);
+			if (at + p.length > Wsg.HS_NEG_MAX_PROTOCOL_BYTES)
+				return null;
+			System.arraycopy(p, 0, b, 48 + at, p.length);
+			at += p.length;
+			b[8 + 2 * (k + 1)] = (byte) at;
+			b[9 + 2 * (k + 1)] = (byte) (at >> 8);
+		}
+		return b;
+	}
+
+	/** Handshaker.accept for n requests (Wsg.handshakeAcceptBatchHost's buffers, plus `negotiated`). */
+	int accept(long ctx, int[] config, ByteBuffer req, ByteBuffer reqOff, int n, ByteBuffer resp, ByteBuffer result,
+			ByteBuffer negotiated) {
+		return Wsg.handshakeAcceptNegotiateBatchHost(ctx, config, image, req, reqOff, n, resp, result, negotiated);
+	}
+
+	/** Handshaker.validate for n responses (Wsg.handshakeValidateBatchHost's buffers, plus `negotiated`). */
+	int validate(long ctx, int[] config, ByteBuffer resp, ByteBuffer respOff, ByteBuffer keys, int n,
+			ByteBuffer expected, ByteBuffer result, ByteBuffer negotiated) {
+		return Wsg.handshakeValidateNegotiateBatchHost(ctx, config, image, resp, respOff, keys, n, expected, result,
+				negotiated);
 	}
 }

@@ -210,6 +210,23 @@ final class Wsg {
 	static native int handshakeValidateBatchHost(long ctx, int[] config, ByteBuffer resp, ByteBuffer respOff,
 			ByteBuffer keys, int n, ByteBuffer expected, ByteBuffer result);
 
+	/* ---- the same with the negotiation decided on the device:
+	 * wsg_handshake_accept_negotiate_batch_host / wsg_handshake_validate_negotiate_batch_host.
+	 * negotiation = the HS_NEGOTIATION_BYTES image of wsg_hs_negotiation
+	 * (GpuHandshakeNegotiator.pack()); resp holds HS_NEG_RESP_STRIDE bytes per request;
+	 * negotiated receives 8-byte wsg_hs_negotiated records. ---- */
+	static final int HS_NEGOTIATION_BYTES = 304;
+	static final int HS_NEG_RESP_STRIDE = 384;
+	static final int HS_NEG_MAX_PROTOCOLS = 16;
+	static final int HS_NEG_MAX_PROTOCOL_BYTES = 256;
+
+	static native int handshakeAcceptNegotiateBatchHost(long ctx, int[] config, byte[] negotiation, ByteBuffer req,
+			ByteBuffer reqOff, int n, ByteBuffer resp, ByteBuffer result, ByteBuffer negotiated);
+
+	static native int handshakeValidateNegotiateBatchHost(long ctx, int[] config, byte[] negotiation,
+			ByteBuffer resp, ByteBuffer respOff, ByteBuffer keys, int n, ByteBuffer expected, ByteBuffer result,
+			ByteBuffer negotiated);
+
 	/* ---- pinned host pool: wsg_host_alloc / wsg_host_release ---- */
 	static native ByteBuffer allocPinned(int capacity);
 

@@ -632,6 +632,51 @@ JNIEXPORT jint JNICALL Java_org_snf4j_websocket_gpu_Wsg_handshakeValidateBatchHo
     return wsg_handshake_validate_batch_host(CTX(ctx), &cfg, rs, off, k, (uint32_t)n, ex, res);
 }
 
+/* negotiation = the wsg_hs_negotiation image GpuHandshakeNegotiator.pack() builds (little-endian,
+ * sizeof(wsg_hs_negotiation) bytes); the library checks its contents */
+static int hs_negotiation(JNIEnv* env, jbyteArray a, wsg_hs_negotiation* g) {
+    if (!a || (*env)->GetArrayLength(env, a) != (jsize)sizeof *g) return 0;
+    (*env)->GetByteArrayRegion(env, a, 0, (jsize)sizeof *g, (jbyte*)g);
+    return 1;
+}
+
+JNIEXPORT jint JNICALL Java_org_snf4j_websocket_gpu_Wsg_handshakeAcceptNegotiateBatchHost(
+        JNIEnv* env, jclass c, jlong ctx, jintArray config, jbyteArray negotiation, jobject req, jobject req_off,
+        jint n, jobject resp, jobject result, jobject negotiated) {
+    (void)c;
+    if (!ctx || n < 0) return WSG_API_EINVAL;
+    const uint64_t* off = NULL;
+    const uint8_t* rq = hs_input(env, req, req_off, n, &off);
+    uint8_t* rs = span(env, resp, (uint64_t)n * WSG_HS_NEG_RESP_STRIDE);
+    wsg_hs_result* res = (wsg_hs_result*)span(env, result, (uint64_t)n * sizeof(wsg_hs_result));
+    wsg_hs_negotiated* ng = (wsg_hs_negotiated*)span(env, negotiated, (uint64_t)n * sizeof(wsg_hs_negotiated));
+    if (!rq || (n && (!rs || !res || !ng))) return WSG_API_EINVAL;
+    wsg_hs_config cfg;
+    wsg_hs_negotiation neg;
+    hs_config(env, config, &cfg);
+    if (!hs_negotiation(env, negotiation, &neg)) return WSG_API_EINVAL;
+    return wsg_handshake_accept_negotiate_batch_host(CTX(ctx), &cfg, &neg, rq, off, (uint32_t)n, rs, res, ng);
+}
+
+JNIEXPORT jint JNICALL Java_org_snf4j_websocket_gpu_Wsg_handshakeValidateNegotiateBatchHost(
+        JNIEnv* env, jclass c, jlong ctx, jintArray config, jbyteArray negotiation, jobject resp, jobject resp_off,
+        jobject keys, jint n, jobject expected, jobject result, jobject negotiated) {
+    (void)c;
+    if (!ctx || n < 0) return WSG_API_EINVAL;
+    const uint64_t* off = NULL;
+    const uint8_t* rs = hs_input(env, resp, resp_off, n, &off);
+    const uint8_t* k = span(env, keys, (uint64_t)n * 24);
+    uint8_t* ex = span(env, expected, (uint64_t)n * WSG_HS_EXPECTED_STRIDE);
+    wsg_hs_result* res = (wsg_hs_result*)span(env, result, (uint64_t)n * sizeof(wsg_hs_result));
+    wsg_hs_negotiated* ng = (wsg_hs_negotiated*)span(env, negotiated, (uint64_t)n * sizeof(wsg_hs_negotiated));
+    if (!rs || (n && (!k || !ex || !res || !ng))) return WSG_API_EINVAL;
+    wsg_hs_config cfg;
+    wsg_hs_negotiation neg;
+    hs_config(env, config, &cfg);
+    if (!hs_negotiation(env, negotiation, &neg)) return WSG_API_EINVAL;
+    return wsg_handshake_validate_negotiate_batch_host(CTX(ctx), &cfg, &neg, rs, off, k, (uint32_t)n, ex, res, ng);
+}
+
 /* ---- pinned host pool (IByteBufferAllocator.allocate / release) ---- */
 JNIEXPORT jobject JNICALL Java_org_snf4j_websocket_gpu_Wsg_allocPinned(JNIEnv* env, jclass c, jint capacity) {
     (void)c;

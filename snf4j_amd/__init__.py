@@ -10,8 +10,8 @@ from . import _lib  # noqa: F401  (fails loudly if libwsgpu.so is missing)
 from .codec import (BatchAggregator, BatchInflater, EncodeBatcher, FrameAggregator, FrameDecoder, FrameEncoder,
                     FrameUtf8Validator, NativeBatcher, PerMessageDeflateDecoder, SessionBatcher)
 from .context import Context, decoder_cfg, encoded_length, error_message, frame_available
-from .handshake import (BatchClientHandshaker, BatchHandshaker, ClientConfig, ClientHandshakeOutcome, HandshakeConfig,
-                        HandshakeOutcome)
+from .handshake import (BatchClientHandshaker, BatchHandshaker, ClientConfig, ClientHandshakeOutcome,
+                        DeflateNegotiation, HandshakeConfig, HandshakeOutcome, Negotiation)
 from .frame import (AggregatedBinaryFrame, AggregatedTextFrame, BinaryFrame, CloseFrame, ContinuationFrame, Frame,
                     InvalidFrameException, Opcode, PingFrame, PongFrame, TextFrame)
 
@@ -19,5 +19,5 @@ __all__ = ["Context", "FrameDecoder", "FrameEncoder", "EncodeBatcher", "SessionB
            "FrameUtf8Validator", "NativeBatcher", "BatchInflater", "PerMessageDeflateDecoder",
            "AggregatedTextFrame", "AggregatedBinaryFrame", "decoder_cfg", "encoded_length",
            "error_message", "frame_available",
-           "BatchHandshaker", "HandshakeConfig", "HandshakeOutcome", "Frame", "Opcode", "TextFrame", "BinaryFrame", "ContinuationFrame",
+           "BatchHandshaker", "HandshakeConfig", "HandshakeOutcome", "Negotiation", "DeflateNegotiation", "Frame", "Opcode", "TextFrame", "BinaryFrame", "ContinuationFrame",
            "CloseFrame", "PingFrame", "PongFrame", "InvalidFrameException"]

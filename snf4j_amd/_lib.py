@@ -67,13 +67,26 @@ class HsConfig(C.Structure):
                 ("extensions", C.c_uint8), ("host_policy", C.c_uint8)]
 
 
+class HsNegotiation(C.Structure):
+    """wsg_hs_negotiation: what wsg_handshake_*_negotiate_batch_* decide on the device."""
+    _fields_ = [("n_protocols", C.c_uint8), ("deflate", C.c_uint8), ("other_extensions", C.c_uint8),
+                ("compress_no_context", C.c_uint8), ("decompress_no_context", C.c_uint8),
+                ("reserved", C.c_uint8 * 3), ("protocol_off", C.c_uint16 * 17), ("reserved2", C.c_uint8 * 6),
+                ("protocol_bytes", C.c_uint8 * 256)]
+
+
 BATCHER_MAX_INFLIGHT = 4  # WSG_BATCHER_MAX_INFLIGHT: decode flushes a batcher keeps in flight
 HS_RESP_STRIDE = 160
 HS_EXPECTED_STRIDE = 32   # wsg_handshake_validate_batch_*: expected Sec-WebSocket-Accept per session
+HS_NEG_RESP_STRIDE = 384  # WSG_HS_NEG_RESP_STRIDE: response bytes per request of the negotiating accept
+HS_NEG_MAX_TOKEN = 96     # WSG_HS_NEG_MAX_TOKEN
+HS_NEG_MAX_PROTOCOLS, HS_NEG_MAX_PROTOCOL_BYTES = 16, 256
+HS_EXT_DEFLATE, HS_EXT_CLIENT_NO_CONTEXT, HS_EXT_SERVER_NO_CONTEXT = 1, 2, 4
 
 
 assert C.sizeof(SessionState) == 8 and C.sizeof(FrameDesc) == 16
 assert C.sizeof(SessionResult) == 16 and C.sizeof(EncodeFrame) == 24
+assert C.sizeof(HsNegotiation) == 304
 
 # numpy views of the same records
 try:
@@ -97,6 +110,8 @@ try:
     HS_RESULT_DTYPE = np.dtype([("frame_len", "<u4"), ("http_status", "<u2"), ("kind", "u1"), ("cause", "u1"),
                                 ("resp_len", "<u2"), ("detail_len", "<u2"), ("detail_off", "<u4")])
     assert HS_RESULT_DTYPE.itemsize == 16
+    HS_NEGOTIATED_DTYPE = np.dtype([("proto_off", "<u4"), ("proto_len", "<u2"), ("ext", "u1"), ("reserved", "u1")])
+    assert HS_NEGOTIATED_DTYPE.itemsize == 8
 except ImportError:  # pragma: no cover
     np = None
 
@@ -194,6 +209,12 @@ def _load():
         "wsg_handshake_accept_batch_host": ([p, P(HsConfig), p, p, u32, p, p], i32),
         "wsg_handshake_validate_batch_device": ([p, P(HsConfig), p, p, p, u32, p, p], i32),
         "wsg_handshake_validate_batch_host": ([p, P(HsConfig), p, p, p, u32, p, p], i32),
+        "wsg_handshake_accept_negotiate_batch_device": ([p, P(HsConfig), P(HsNegotiation), p, p, u32, p, p, p], i32),
+        "wsg_handshake_accept_negotiate_batch_host": ([p, P(HsConfig), P(HsNegotiation), p, p, u32, p, p, p], i32),
+        "wsg_handshake_validate_negotiate_batch_device": ([p, P(HsConfig), P(HsNegotiation), p, p, p, u32, p, p, p],
+                                                          i32),
+        "wsg_handshake_validate_negotiate_batch_host": ([p, P(HsConfig), P(HsNegotiation), p, p, p, u32, p, p, p],
+                                                        i32),
     }
     for name, (args, res) in sig.items():
         f = getattr(L, name)

@@ -352,6 +352,53 @@ class Context:
                                                     k.ctypes.data, n, exp.ctypes.data, res.ctypes.data), self._h)
         return exp[:n], res[:n]
 
+    def handshake_accept_negotiate_device(self, cfg, neg, req, req_off, resp, result, negotiated,
+                                          n: int | None = None):
+        """handshake_accept_device with the negotiation on the device
+        (wsg_handshake_accept_negotiate_batch_device): neg an HsNegotiation, resp uint8
+        (n * HS_NEG_RESP_STRIDE), negotiated uint8 byte view (n * 8)."""
+        n = req_off.numel() - 1 if n is None else int(n)
+        assert resp.numel() >= n * _lib.HS_NEG_RESP_STRIDE and result.numel() >= n * 16 and negotiated.numel() >= n * 8
+        check(lib.wsg_handshake_accept_negotiate_batch_device(self._h, C.byref(cfg), C.byref(neg), _p(req),
+                                                              _p(req_off), n, _p(resp), _p(result),
+                                                              _p(negotiated)), self._h)
+
+    def handshake_accept_negotiate_host(self, cfg, neg, req: np.ndarray, req_off: np.ndarray):
+        """wsg_handshake_accept_negotiate_batch_host.  Returns (resp [n, HS_NEG_RESP_STRIDE] uint8,
+        result HS_RESULT_DTYPE[n], negotiated HS_NEGOTIATED_DTYPE[n])."""
+        from ._lib import HS_NEGOTIATED_DTYPE, HS_RESULT_DTYPE
+        req = np.ascontiguousarray(req, dtype=np.uint8)
+        req_off = np.ascontiguousarray(req_off, dtype=np.uint64)
+        n = len(req_off) - 1
+        resp = np.zeros((max(1, n), _lib.HS_NEG_RESP_STRIDE), dtype=np.uint8)
+        res = np.zeros(max(1, n), dtype=HS_RESULT_DTYPE)
+        ng = np.zeros(max(1, n), dtype=HS_NEGOTIATED_DTYPE)
+        r = req if req.size else np.zeros(16, np.uint8)
+        check(lib.wsg_handshake_accept_negotiate_batch_host(self._h, C.byref(cfg), C.byref(neg), r.ctypes.data,
+                                                            req_off.ctypes.data, n, resp.ctypes.data,
+                                                            res.ctypes.data, ng.ctypes.data), self._h)
+        return resp[:n], res[:n], ng[:n]
+
+    def handshake_validate_negotiate_host(self, cfg, neg, resp: np.ndarray, resp_off: np.ndarray, keys: np.ndarray):
+        """wsg_handshake_validate_negotiate_batch_host.  Returns (expected [n, HS_EXPECTED_STRIDE]
+        uint8, result HS_RESULT_DTYPE[n], negotiated HS_NEGOTIATED_DTYPE[n])."""
+        from ._lib import HS_NEGOTIATED_DTYPE, HS_RESULT_DTYPE
+        resp = np.ascontiguousarray(resp, dtype=np.uint8)
+        resp_off = np.ascontiguousarray(resp_off, dtype=np.uint64)
+        keys = np.ascontiguousarray(keys, dtype=np.uint8).reshape(-1)
+        n = len(resp_off) - 1
+        assert keys.size >= n * 24
+        exp = np.zeros((max(1, n), _lib.HS_EXPECTED_STRIDE), dtype=np.uint8)
+        res = np.zeros(max(1, n), dtype=HS_RESULT_DTYPE)
+        ng = np.zeros(max(1, n), dtype=HS_NEGOTIATED_DTYPE)
+        r = resp if resp.size else np.zeros(16, np.uint8)
+        k = keys if keys.size else np.zeros(24, np.uint8)
+        check(lib.wsg_handshake_validate_negotiate_batch_host(self._h, C.byref(cfg), C.byref(neg), r.ctypes.data,
+                                                              resp_off.ctypes.data, k.ctypes.data, n,
+                                                              exp.ctypes.data, res.ctypes.data, ng.ctypes.data),
+              self._h)
+        return exp[:n], res[:n], ng[:n]
+
     # -------------------------------------------------------------- aggregate
     def aggregate_device(self, max_aggregated_len: int, desc, session_first, dec_result, payload, state, agg_out,
                          out_desc, out_result, agg_total, n_frames: int | None = None):

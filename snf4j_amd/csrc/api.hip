@@ -22,7 +22,8 @@ const char* const kKernelNames[K_COUNT] = {"k_parse",   "k_scan",     "k_link", 
                                            "k_final",    "k_enc_len",  "k_enc_scan",
                                            "k_enc_piecesN", "k_enc_final", "k_enc_desc", "k_agg_plan", "k_agg_gather", "k_inflate", "k_hs_accept", "k_infl_tok", "k_infl_fast", "k_hs_validate",
                                            "k_defl_plan", "k_defl_prep", "k_defl_match", "k_defl_parse", "k_defl_final", "k_defl_serial",
-                                           "k_defl_trees", "k_defl_emit", "k_defl_hist", "k_defl_match_lds", "k_defl_links"};
+                                           "k_defl_trees", "k_defl_emit", "k_defl_hist", "k_defl_match_lds", "k_defl_links",
+                                           "k_hs_accept_neg", "k_hs_validate_neg"};
 
 struct DevBuf {
   void* p = nullptr;
@@ -161,7 +162,7 @@ template <typename F>
 static void timed(wsg_ctx* c, int kid, F&& f) {
   // an event pair costs a few microseconds of queue time: mode 2 brackets only the
   // streaming kernels, so a timed step keeps the side kernels back to back
-  if (!c->timing || (c->timing == 2 && kid != K_UNMASK && kid != K_ENC_EMIT && kid != K_AGG_GATHER && kid != K_INFLATE && kid != K_HS_ACCEPT && kid != K_HS_VALIDATE && kid != K_INFL_TOK && kid != K_INFL_FAST && kid != K_DEFL_MATCH && kid != K_DEFL_PARSE && kid != K_DEFL_PREP && kid != K_DEFL_SERIAL && kid != K_DEFL_TREES && kid != K_DEFL_MATCH_LDS && kid != K_DEFL_LINKS &&
+  if (!c->timing || (c->timing == 2 && kid != K_UNMASK && kid != K_ENC_EMIT && kid != K_AGG_GATHER && kid != K_INFLATE && kid != K_HS_ACCEPT && kid != K_HS_VALIDATE && kid != K_HS_ACCEPT_NEG && kid != K_HS_VALIDATE_NEG && kid != K_INFL_TOK && kid != K_INFL_FAST && kid != K_DEFL_MATCH && kid != K_DEFL_PARSE && kid != K_DEFL_PREP && kid != K_DEFL_SERIAL && kid != K_DEFL_TREES && kid != K_DEFL_MATCH_LDS && kid != K_DEFL_LINKS &&
                                  kid != K_DEFL_EMIT && kid != K_DEFL_HIST)) {
     f();
     return;
@@ -1485,6 +1486,125 @@ int wsg_handshake_validate_batch_host(wsg_ctx* c, const wsg_hs_config* cfg, cons
   if (rc) return rc;
   HIP_TRY(c, hipMemcpyAsync(expected_out, d_exp.p, (uint64_t)n * WSG_HS_EXPECTED_STRIDE, hipMemcpyDeviceToHost, s));
   HIP_TRY(c, hipMemcpyAsync(result, d_res.p, (uint64_t)n * sizeof(wsg_hs_result), hipMemcpyDeviceToHost, s));
+  HIP_TRY(c, hipStreamSynchronize(s));
+  return WSG_API_OK;
+}
+
+// ---- opening handshake with the negotiation on the device (k_hs_accept_neg / k_hs_validate_neg) ----
+
+int wsg_handshake_accept_negotiate_batch_device(wsg_ctx* c, const wsg_hs_config* cfg, const wsg_hs_negotiation* neg,
+                                                const uint8_t* req, const uint64_t* req_off, uint32_t n, uint8_t* resp,
+                                                wsg_hs_result* result, wsg_hs_negotiated* negotiated) {
+  if (!c || !cfg || !neg) return WSG_API_EINVAL;
+  ws::HsNeg packed;
+  if (!ws::hs_neg_pack(*neg, &packed)) return set_err(c, WSG_API_EINVAL, "malformed wsg_hs_negotiation");
+  if (!n) return WSG_API_OK;
+  if (!req || !req_off || !resp || !result || !negotiated) return set_err(c, WSG_API_EINVAL, "null batch pointer");
+  if (((uintptr_t)req & 15) || ((uintptr_t)resp & 15) || ((uintptr_t)negotiated & 7))
+    return set_err(c, WSG_API_EINVAL, "req and resp must be 16-B aligned, negotiated 8-B aligned");
+  HIP_TRY(c, hipSetDevice(c->device));
+  timed(c, K_HS_ACCEPT_NEG,
+        [&] { ws::launch_hs_accept_neg(*cfg, packed, req, req_off, n, resp, result, negotiated, c->stream); });
+  HIP_TRY(c, hipGetLastError());
+  return WSG_API_OK;
+}
+
+int wsg_handshake_accept_negotiate_batch_host(wsg_ctx* c, const wsg_hs_config* cfg, const wsg_hs_negotiation* neg,
+                                              const uint8_t* req, const uint64_t* req_off, uint32_t n, uint8_t* resp,
+                                              wsg_hs_result* result, wsg_hs_negotiated* negotiated) {
+  if (!c || !cfg || !neg) return WSG_API_EINVAL;
+  ws::HsNeg packed;
+  if (!ws::hs_neg_pack(*neg, &packed)) return set_err(c, WSG_API_EINVAL, "malformed wsg_hs_negotiation");
+  if (!n) return WSG_API_OK;
+  if (!req_off || !resp || !result || !negotiated) return set_err(c, WSG_API_EINVAL, "null batch pointer");
+  for (uint32_t i = 0; i < n; ++i)
+    if (req_off[i + 1] < req_off[i]) return set_err(c, WSG_API_EINVAL, "req_off not ascending at %u", i);
+  if (req_off[0] != 0) return set_err(c, WSG_API_EINVAL, "req_off[0] must be 0");
+  HIP_TRY(c, hipSetDevice(c->device));
+  const uint64_t len = req_off[n];
+  DevBuf d_req, d_off, d_resp, d_res, d_neg;
+  struct Guard {
+    DevBuf* b[5];
+    ~Guard() { for (DevBuf* x : b) x->release(); }
+  } g{{&d_req, &d_off, &d_resp, &d_res, &d_neg}};
+  HIP_TRY(c, d_req.ensure(len + 16));
+  HIP_TRY(c, d_off.ensure(((uint64_t)n + 1) * sizeof(uint64_t)));
+  HIP_TRY(c, d_resp.ensure((uint64_t)n * WSG_HS_NEG_RESP_STRIDE));
+  HIP_TRY(c, d_res.ensure((uint64_t)n * sizeof(wsg_hs_result)));
+  HIP_TRY(c, d_neg.ensure((uint64_t)n * sizeof(wsg_hs_negotiated)));
+  hipStream_t s = c->stream;
+  if (len) HIP_TRY(c, hipMemcpyAsync(d_req.p, req, len, hipMemcpyHostToDevice, s));
+  HIP_TRY(c, hipMemcpyAsync(d_off.p, req_off, ((uint64_t)n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, s));
+  int rc = wsg_handshake_accept_negotiate_batch_device(c, cfg, neg, (const uint8_t*)d_req.p, (const uint64_t*)d_off.p,
+                                                       n, (uint8_t*)d_resp.p, (wsg_hs_result*)d_res.p,
+                                                       (wsg_hs_negotiated*)d_neg.p);
+  if (rc) return rc;
+  HIP_TRY(c, hipMemcpyAsync(resp, d_resp.p, (uint64_t)n * WSG_HS_NEG_RESP_STRIDE, hipMemcpyDeviceToHost, s));
+  HIP_TRY(c, hipMemcpyAsync(result, d_res.p, (uint64_t)n * sizeof(wsg_hs_result), hipMemcpyDeviceToHost, s));
+  HIP_TRY(c, hipMemcpyAsync(negotiated, d_neg.p, (uint64_t)n * sizeof(wsg_hs_negotiated), hipMemcpyDeviceToHost, s));
+  HIP_TRY(c, hipStreamSynchronize(s));
+  return WSG_API_OK;
+}
+
+int wsg_handshake_validate_negotiate_batch_device(wsg_ctx* c, const wsg_hs_config* cfg, const wsg_hs_negotiation* neg,
+                                                  const uint8_t* resp, const uint64_t* resp_off, const uint8_t* keys,
+                                                  uint32_t n, uint8_t* expected_out, wsg_hs_result* result,
+                                                  wsg_hs_negotiated* negotiated) {
+  if (!c || !cfg || !neg) return WSG_API_EINVAL;
+  ws::HsNeg packed;
+  if (!ws::hs_neg_pack(*neg, &packed)) return set_err(c, WSG_API_EINVAL, "malformed wsg_hs_negotiation");
+  if (!n) return WSG_API_OK;
+  if (!resp || !resp_off || !keys || !expected_out || !result || !negotiated)
+    return set_err(c, WSG_API_EINVAL, "null batch pointer");
+  if (((uintptr_t)resp & 15) || ((uintptr_t)expected_out & 15) || ((uintptr_t)keys & 3) || ((uintptr_t)negotiated & 7))
+    return set_err(c, WSG_API_EINVAL,
+                   "resp and expected_out must be 16-B aligned, keys 4-B aligned, negotiated 8-B aligned");
+  HIP_TRY(c, hipSetDevice(c->device));
+  timed(c, K_HS_VALIDATE_NEG, [&] {
+    ws::launch_hs_validate_neg(*cfg, packed, resp, resp_off, keys, n, expected_out, result, negotiated, c->stream);
+  });
+  HIP_TRY(c, hipGetLastError());
+  return WSG_API_OK;
+}
+
+int wsg_handshake_validate_negotiate_batch_host(wsg_ctx* c, const wsg_hs_config* cfg, const wsg_hs_negotiation* neg,
+                                                const uint8_t* resp, const uint64_t* resp_off, const uint8_t* keys,
+                                                uint32_t n, uint8_t* expected_out, wsg_hs_result* result,
+                                                wsg_hs_negotiated* negotiated) {
+  if (!c || !cfg || !neg) return WSG_API_EINVAL;
+  ws::HsNeg packed;
+  if (!ws::hs_neg_pack(*neg, &packed)) return set_err(c, WSG_API_EINVAL, "malformed wsg_hs_negotiation");
+  if (!n) return WSG_API_OK;
+  if (!resp_off || !keys || !expected_out || !result || !negotiated)
+    return set_err(c, WSG_API_EINVAL, "null batch pointer");
+  for (uint32_t i = 0; i < n; ++i)
+    if (resp_off[i + 1] < resp_off[i]) return set_err(c, WSG_API_EINVAL, "resp_off not ascending at %u", i);
+  if (resp_off[0] != 0) return set_err(c, WSG_API_EINVAL, "resp_off[0] must be 0");
+  HIP_TRY(c, hipSetDevice(c->device));
+  const uint64_t len = resp_off[n];
+  DevBuf d_resp, d_off, d_keys, d_exp, d_res, d_neg;
+  struct Guard {
+    DevBuf* b[6];
+    ~Guard() { for (DevBuf* x : b) x->release(); }
+  } g{{&d_resp, &d_off, &d_keys, &d_exp, &d_res, &d_neg}};
+  HIP_TRY(c, d_resp.ensure(len + 16));
+  HIP_TRY(c, d_off.ensure(((uint64_t)n + 1) * sizeof(uint64_t)));
+  HIP_TRY(c, d_keys.ensure((uint64_t)n * 24));
+  HIP_TRY(c, d_exp.ensure((uint64_t)n * WSG_HS_EXPECTED_STRIDE));
+  HIP_TRY(c, d_res.ensure((uint64_t)n * sizeof(wsg_hs_result)));
+  HIP_TRY(c, d_neg.ensure((uint64_t)n * sizeof(wsg_hs_negotiated)));
+  hipStream_t s = c->stream;
+  if (len) HIP_TRY(c, hipMemcpyAsync(d_resp.p, resp, len, hipMemcpyHostToDevice, s));
+  HIP_TRY(c, hipMemcpyAsync(d_off.p, resp_off, ((uint64_t)n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, s));
+  HIP_TRY(c, hipMemcpyAsync(d_keys.p, keys, (uint64_t)n * 24, hipMemcpyHostToDevice, s));
+  int rc = wsg_handshake_validate_negotiate_batch_device(c, cfg, neg, (const uint8_t*)d_resp.p,
+                                                         (const uint64_t*)d_off.p, (const uint8_t*)d_keys.p, n,
+                                                         (uint8_t*)d_exp.p, (wsg_hs_result*)d_res.p,
+                                                         (wsg_hs_negotiated*)d_neg.p);
+  if (rc) return rc;
+  HIP_TRY(c, hipMemcpyAsync(expected_out, d_exp.p, (uint64_t)n * WSG_HS_EXPECTED_STRIDE, hipMemcpyDeviceToHost, s));
+  HIP_TRY(c, hipMemcpyAsync(result, d_res.p, (uint64_t)n * sizeof(wsg_hs_result), hipMemcpyDeviceToHost, s));
+  HIP_TRY(c, hipMemcpyAsync(negotiated, d_neg.p, (uint64_t)n * sizeof(wsg_hs_negotiated), hipMemcpyDeviceToHost, s));
   HIP_TRY(c, hipStreamSynchronize(s));
   return WSG_API_OK;
 }

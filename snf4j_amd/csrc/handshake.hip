@@ -11,6 +11,8 @@
 // lines the first pass brought in).  No LDS, no cross-lane traffic.  The lane
 // decides every request whose form it can reproduce exactly and defers the rest to
 // the Java Handshaker (wsgpu.h lists the deferred forms).
+#include <string.h>
+
 #include <type_traits>
 
 #include "wsgpu_internal.h"
@@ -362,6 +364,37 @@ struct Out {
   __device__ void put(const uint8_t* s, int len) {
     for (int i = 0; i < len; ++i) byte(s[i]);
   }
+  // Up to four bytes (the low `cnt` of w, the rest zero) at a position known only at
+  // run time: one shift into the block instead of a branch per byte.
+  __device__ __forceinline__ void word(uint32_t w, int cnt) {
+    const int k = n & 15;
+    const uint64_t v = w;
+    if (k < 8) {
+      lo |= v << (8 * k);
+      if (k > 4) hi |= v >> (8 * (8 - k));
+    } else {
+      hi |= v << (8 * (k - 8));  // (bytes past the block fall off: carried below)
+    }
+    if (k + cnt >= 16) {
+      reinterpret_cast<uint4*>(p)[n >> 4] = make_uint4((uint32_t)lo, (uint32_t)(lo >> 32), (uint32_t)hi, (uint32_t)(hi >> 32));
+      lo = k + cnt > 16 ? v >> (8 * (16 - k)) : 0;
+      hi = 0;
+    }
+    n += cnt;
+  }
+  // A literal after a part of run-time length: its dwords are immediates (put() would
+  // load every byte from constant memory once the position is no constant).
+  template <int N>
+  __device__ __forceinline__ void lit(const char (&s)[N]) {
+#pragma unroll
+    for (int i = 0; i < N - 1; i += 4) {
+      uint32_t w = 0;
+#pragma unroll
+      for (int q = 0; q < 4; ++q)
+        if (i + q < N - 1) w |= (uint32_t)(uint8_t)s[i + q] << (8 * q);
+      word(w, N - 1 - i < 4 ? N - 1 - i : 4);
+    }
+  }
   __device__ int done() {
     if (n & 15)
       reinterpret_cast<uint4*>(p)[n >> 4] = make_uint4((uint32_t)lo, (uint32_t)(lo >> 32), (uint32_t)hi, (uint32_t)(hi >> 32));
@@ -423,7 +456,165 @@ __host__ __device__ int hs_frame_len(const uint8_t* d, int64_t len, int* capped,
 
 namespace {
 
-__device__ __forceinline__ void accept_one(Req& d, int64_t n, const wsg_hs_config& cfg, uint8_t* resp, wsg_hs_result* res) {
+// ------------------------------------------------------------------ negotiation
+// The string work of Handshaker.acceptSubProtocol / acceptExtensions and their client
+// counterparts for a config of subprotocols and one PerMessageDeflateExtension
+// (k_hs_accept_neg / k_hs_validate_neg).  The settings are a kernel argument (HsNeg by
+// value): uniform, so its reads are scalar.  Everything works on Spans of the request.
+struct NoNeg {};  // the settings type of the kernels that defer instead (k_hs_accept / k_hs_validate)
+
+__device__ __forceinline__ uint32_t neg_byte(const HsNeg& g, uint32_t j) {
+  return (g.words[j >> 2] >> (8u * (j & 3u))) & 0xffu;
+}
+
+// t equals a supported subprotocol, byte for byte.  Both loops run over the settings
+// only (no early exit), so their counters and the blob's dwords stay scalar.
+__device__ __forceinline__ bool proto_supported(Req& d, Span t, const HsNeg& g) {
+  bool any = false;
+  for (uint32_t k = 0; k < g.n_protocols; ++k) {
+    const uint32_t b = g.off[k], len = g.off[k + 1] - b;
+    if ((uint32_t)(t.e - t.b) != len) continue;
+    bool m = true;
+    for (uint32_t j = 0; j < len; ++j) m &= d[t.b + (int32_t)j] == neg_byte(g, b + j);
+    any |= m;
+  }
+  return any;
+}
+
+// HttpUtils.values(s, ";") (HttpUtils.java:319-334): each_value with another separator.
+template <typename F>
+__device__ __forceinline__ void each_item(Req& d, Span s, F&& f) {
+  int32_t t0 = s.b;
+  for (int32_t i = s.b; i <= s.e; ++i) {
+    if (i == s.e || d[i] == ';') {
+      const Span t = trim(d, Span{t0, i});
+      if (t.e > t.b && f(t)) return;
+      t0 = i + 1;
+    }
+  }
+}
+
+// What PerMessageDeflateParams.parse found in one extension.
+enum : uint32_t {
+  PMD_CLIENT_NC = 1u,   // client_no_context_takeover
+  PMD_SERVER_NC = 2u,   // server_no_context_takeover
+  PMD_CLIENT_MW = 4u,   // client_max_window_bits (with or without a value)
+  PMD_SERVER_MW = 8u,   // server_max_window_bits
+  PMD_CLIENT_MW_LOW = 16u,  // getClientMaxWindow() < 15: a value of 8..14, or none (NO_VALUE is -1)
+  PMD_SERVER_MW_LOW = 32u,  // getServerMaxWindow() < 15: a value of 8..14
+};
+
+// HandshakeUtils.extension(String) (HandshakeUtils.java:195-228) + wrongName
+// (PerMessageDeflateExtension.java:177-179) + PerMessageDeflateParams.parse (:124-154)
+// over one element of Sec-WebSocket-Extensions.  Returns -1 when the name is not
+// permessage-deflate (nothing is parsed then), 0 with *found set, or the WSG_HSC_EXT_*
+// cause of the InvalidExtensionException.
+__device__ __forceinline__ int pmd_parse(Req& d, Span ext, uint32_t* found) {
+  int item_no = 0, verdict = -1;
+  uint32_t bits = 0u;
+  each_item(d, ext, [&](Span it) {
+    if (item_no++ == 0) {
+      if (!eq_exact(d, it, "permessage-deflate", 18)) return true;
+      verdict = 0;
+      return false;
+    }
+    // "name[=value]": the first '=' splits; both sides trimmed, one pair of quotes taken
+    // off a value longer than one character (and not trimmed again)
+    int32_t eq = -1;
+    for (int32_t j = it.b; j < it.e; ++j)
+      if (d[j] == '=') {
+        eq = j;
+        break;
+      }
+    const bool has_value = eq >= 0;
+    Span name = it, val{it.e, it.e};
+    if (has_value) {
+      name = trim(d, Span{it.b, eq});
+      val = trim(d, Span{eq + 1, it.e});
+      if (val.e - val.b > 1 && d[val.b] == '"' && d[val.e - 1] == '"') {
+        ++val.b;
+        --val.e;
+      }
+    }
+    uint32_t bit = 0u;  // equalsIgnoreCase against the four names
+    if (eq_icase(d, name, "CLIENT_NO_CONTEXT_TAKEOVER", 26)) bit = PMD_CLIENT_NC;
+    else if (eq_icase(d, name, "SERVER_NO_CONTEXT_TAKEOVER", 26)) bit = PMD_SERVER_NC;
+    else if (eq_icase(d, name, "CLIENT_MAX_WINDOW_BITS", 22)) bit = PMD_CLIENT_MW;
+    else if (eq_icase(d, name, "SERVER_MAX_WINDOW_BITS", 22)) bit = PMD_SERVER_MW;
+    if (!bit) {
+      verdict = WSG_HSC_EXT_UNEXPECTED;
+      return true;
+    }
+    if (bits & bit) {  // set / setInt (:83-122): duplicate, then the value's presence, format, range
+      verdict = WSG_HSC_EXT_DUPLICATED;
+      return true;
+    }
+    bits |= bit;
+    if (bit & (PMD_CLIENT_NC | PMD_SERVER_NC)) {
+      if (has_value) {
+        verdict = WSG_HSC_EXT_UNNECESSARY_VALUE;
+        return true;
+      }
+      return false;
+    }
+    if (!has_value) {
+      if (bit == PMD_SERVER_MW) {
+        verdict = WSG_HSC_EXT_MISSING_VALUE;
+        return true;
+      }
+      bits |= PMD_CLIENT_MW_LOW;
+      return false;
+    }
+    int64_t v = 0;
+    if (val.e <= val.b || !parse_int(d, val, &v)) {
+      verdict = WSG_HSC_EXT_VALUE_FORMAT;
+      return true;
+    }
+    if (v < 8 || v > 15) {  // checkBits (:79-81)
+      verdict = WSG_HSC_EXT_VALUE;
+      return true;
+    }
+    if (v < 15) bits |= bit == PMD_CLIENT_MW ? PMD_CLIENT_MW_LOW : PMD_SERVER_MW_LOW;
+    return false;
+  });
+  *found = bits;
+  return verdict;
+}
+
+// PerMessageDeflateExtension.acceptOffer (:182-223) after parse: WSG_HS_EXT_* of the
+// accepted extension, or 0 when the offer is declined.
+__device__ __forceinline__ uint32_t pmd_accept_offer(const HsNeg& g, uint32_t p) {
+  const bool cnc = p & PMD_CLIENT_NC, snc = p & PMD_SERVER_NC;
+  if ((cnc && g.decompress_no_context == WSG_HS_NOCONTEXT_FORBIDDEN) ||
+      (snc && g.compress_no_context == WSG_HS_NOCONTEXT_FORBIDDEN) || (p & PMD_SERVER_MW_LOW))
+    return 0u;
+  return WSG_HS_EXT_DEFLATE |
+         ((cnc || g.decompress_no_context == WSG_HS_NOCONTEXT_REQUIRED) ? WSG_HS_EXT_CLIENT_NO_CONTEXT : 0u) |
+         ((snc || g.compress_no_context == WSG_HS_NOCONTEXT_REQUIRED) ? WSG_HS_EXT_SERVER_NO_CONTEXT : 0u);
+}
+
+// PerMessageDeflateExtension.validateResponse (:226-267) after parse: a side that is
+// REQUIRED and absent declines too, and so does client_max_window_bits below 15.
+__device__ __forceinline__ uint32_t pmd_validate_response(const HsNeg& g, uint32_t p) {
+  const bool cnc = p & PMD_CLIENT_NC, snc = p & PMD_SERVER_NC;
+  if (g.compress_no_context == (cnc ? WSG_HS_NOCONTEXT_FORBIDDEN : WSG_HS_NOCONTEXT_REQUIRED) ||
+      g.decompress_no_context == (snc ? WSG_HS_NOCONTEXT_FORBIDDEN : WSG_HS_NOCONTEXT_REQUIRED) ||
+      (p & PMD_CLIENT_MW_LOW))
+    return 0u;
+  return WSG_HS_EXT_DEFLATE | (cnc ? WSG_HS_EXT_CLIENT_NO_CONTEXT : 0u) | (snc ? WSG_HS_EXT_SERVER_NO_CONTEXT : 0u);
+}
+
+// one 8-B store of a wsg_hs_negotiated
+__device__ __forceinline__ void put_negotiated(wsg_hs_negotiated* out, Span proto, uint32_t ext) {
+  const uint32_t len = proto.b >= 0 ? (uint32_t)(proto.e - proto.b) : 0u;
+  *reinterpret_cast<uint2*>(out) = make_uint2(len ? (uint32_t)proto.b : 0u, len | (ext << 16));
+}
+
+// NEG: decide subprotocol and extension offers with the settings `neg` (HsNeg) instead of
+// deferring them by cfg's flags (`neg` is NoNeg then and nothing of it is read).
+template <bool NEG, class N>
+__device__ __forceinline__ void accept_one(Req& d, int64_t n, const wsg_hs_config& cfg, const N& neg, uint8_t* resp,
+                                           wsg_hs_result* res, wsg_hs_negotiated* negotiated) {
   wsg_hs_result r = {0u, 0, WSG_HS_NEED_MORE, WSG_HSC_NONE, 0, 0, 0u};
   auto finish = [&](int kind, int status, int cause, Span detail) {
     r.kind = (uint8_t)kind;
@@ -436,6 +627,7 @@ __device__ __forceinline__ void accept_one(Req& d, int64_t n, const wsg_hs_confi
     if (kind == WSG_HS_PARSE_ERROR || (kind == WSG_HS_ACCEPT && status != 101))
       r.resp_len = (uint16_t)status_response(resp, status);
     *res = r;
+    if constexpr (NEG) put_negotiated(negotiated, Span{-1, -1}, 0u);
   };
   const Span none{-1, -1};
   int capped = 0;
@@ -654,22 +846,78 @@ __device__ __forceinline__ void accept_one(Req& d, int64_t n, const wsg_hs_confi
     return;
   }
   // acceptSubProtocol / acceptExtensions (:259-325): only with supported ones configured
-  if (cfg.subprotocols && fld[F_PROTOCOL].b >= 0 && fld[F_PROTOCOL].e > fld[F_PROTOCOL].b) {
-    finish(WSG_HS_DEFER, 0, WSG_HSC_D_SUBPROTOCOL, none);
-    return;
-  }
-  if (cfg.extensions && fld[F_EXTENSIONS].b >= 0 && fld[F_EXTENSIONS].e > fld[F_EXTENSIONS].b) {
-    finish(WSG_HS_DEFER, 0, WSG_HSC_D_EXTENSION, none);
-    return;
+  [[maybe_unused]] Span proto = none;
+  [[maybe_unused]] uint32_t ext = 0u;  // WSG_HS_EXT_* of the accepted offer
+  if constexpr (NEG) {
+    const Span pf = fld[F_PROTOCOL];
+    if (neg.n_protocols && pf.b >= 0 && pf.e > pf.b) {
+      // the first requested token a supported entry equals; "*" takes the first token
+      proto = each_value(d, pf, [&](Span t) { return neg.star || proto_supported(d, t, neg); });
+      if (proto.b >= 0 && proto.e - proto.b > WSG_HS_NEG_MAX_TOKEN) {  // the response slot is not sized for it
+        finish(WSG_HS_DEFER, 0, WSG_HSC_D_SUBPROTOCOL, none);
+        return;
+      }
+    }
+    const Span xf = fld[F_EXTENSIONS];
+    if (xf.b >= 0 && xf.e > xf.b) {
+      if (neg.other_extensions) {  // IExtension.acceptOffer of another class
+        finish(WSG_HS_DEFER, 0, WSG_HSC_D_EXTENSION, none);
+        return;
+      }
+      if (neg.deflate) {
+        // every offer is parsed, also after one was accepted (acceptOffer runs before the
+        // group check, :309-311); the first one not declined is the extension
+        bool invalid = false;
+        each_value(d, xf, [&](Span offer) {
+          uint32_t found = 0u;
+          const int v = pmd_parse(d, offer, &found);
+          if (v > 0) {
+            invalid = true;
+            return true;
+          }
+          if (v == 0 && !ext) ext = pmd_accept_offer(neg, found);
+          return false;
+        });
+        if (invalid) {
+          finish(WSG_HS_ACCEPT, 400, WSG_HSC_INVALID_REQUEST_EXTENSION, none);
+          return;
+        }
+      }
+    }
+  } else {
+    if (cfg.subprotocols && fld[F_PROTOCOL].b >= 0 && fld[F_PROTOCOL].e > fld[F_PROTOCOL].b) {
+      finish(WSG_HS_DEFER, 0, WSG_HSC_D_SUBPROTOCOL, none);
+      return;
+    }
+    if (cfg.extensions && fld[F_EXTENSIONS].b >= 0 && fld[F_EXTENSIONS].e > fld[F_EXTENSIONS].b) {
+      finish(WSG_HS_DEFER, 0, WSG_HSC_D_EXTENSION, none);
+      return;
+    }
   }
   // 101 with Upgrade, Connection, Sec-WebSocket-Accept (:386-391)
   Out o{resp};
   o.put("HTTP/1.1 101 Switching Protocols\r\nUpgrade: websocket\r\nConnection: Upgrade\r\nSec-WebSocket-Accept: ");
   accept_key(d, fld[F_KEY], o);  // 28 characters
-  o.put("\r\n\r\n");
+  if constexpr (NEG) {
+    // Sec-WebSocket-Protocol, then Sec-WebSocket-Extensions (:392-403): the extension's
+    // response() joined by HandshakeUtils.extension(List) ("; " between the items)
+    if (proto.b >= 0) {
+      o.lit("\r\nSec-WebSocket-Protocol: ");
+      for (int32_t i = proto.b; i < proto.e; ++i) o.word(d[i], 1);
+    }
+    if (ext) {
+      o.lit("\r\nSec-WebSocket-Extensions: permessage-deflate");
+      if (ext & WSG_HS_EXT_CLIENT_NO_CONTEXT) o.lit("; client_no_context_takeover");
+      if (ext & WSG_HS_EXT_SERVER_NO_CONTEXT) o.lit("; server_no_context_takeover");
+    }
+    o.lit("\r\n\r\n");
+  } else {
+    o.put("\r\n\r\n");
+  }
   const int rl = o.done();
   finish(WSG_HS_ACCEPT, 101, WSG_HSC_NONE, none);
   res->resp_len = (uint16_t)rl;
+  if constexpr (NEG) put_negotiated(negotiated, proto, ext);
 }
 
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WSG_HS_WAVES))) void k_hs_accept(wsg_hs_config cfg, const uint8_t* req, const uint64_t* req_off,
@@ -680,7 +928,23 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WSG_HS_WAVE
   Req d;
   d.base = reinterpret_cast<const uint4*>(req + (b & ~(uint64_t)15));
   d.lead = (uint32_t)(b & 15u);
-  accept_one(d, (int64_t)(e - b), cfg, resp + (uint64_t)i * WSG_HS_RESP_STRIDE, result + i);
+  accept_one<false>(d, (int64_t)(e - b), cfg, NoNeg{}, resp + (uint64_t)i * WSG_HS_RESP_STRIDE, result + i, nullptr);
+}
+
+#ifndef WSG_HS_NEG_WAVES
+#define WSG_HS_NEG_WAVES 5  // 96 VGPRs and k_hs_accept's 8 B of scratch; at 6 waves (80 VGPRs) the parser spills 96 B
+#endif
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WSG_HS_NEG_WAVES))) void k_hs_accept_neg(
+    wsg_hs_config cfg, HsNeg neg, const uint8_t* req, const uint64_t* req_off, uint32_t n, uint8_t* resp,
+    wsg_hs_result* result, wsg_hs_negotiated* negotiated) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const uint64_t b = req_off[i], e = req_off[i + 1];
+  Req d;
+  d.base = reinterpret_cast<const uint4*>(req + (b & ~(uint64_t)15));
+  d.lead = (uint32_t)(b & 15u);
+  accept_one<true>(d, (int64_t)(e - b), cfg, neg, resp + (uint64_t)i * WSG_HS_NEG_RESP_STRIDE, result + i,
+                   negotiated + i);
 }
 
 // ------------------------------------------------------------------ client side
@@ -725,9 +989,13 @@ struct KeySink {
   }
 };
 
-__device__ __forceinline__ void validate_one(Req& d, int64_t n, const wsg_hs_config& cfg, const KeyWords& key,
-                                             uint8_t* expected, wsg_hs_result* res) {
+template <bool NEG, class N>
+__device__ __forceinline__ void validate_one(Req& d, int64_t n, const wsg_hs_config& cfg, const N& neg,
+                                             const KeyWords& key, uint8_t* expected, wsg_hs_result* res,
+                                             wsg_hs_negotiated* negotiated) {
   wsg_hs_result r = {0u, 0, WSG_HS_NEED_MORE, WSG_HSC_NONE, 0, 0, 0u};
+  [[maybe_unused]] Span proto{-1, -1};
+  [[maybe_unused]] uint32_t ext = 0u;  // WSG_HS_EXT_* of the validated answer
   auto finish = [&](int kind, int cause, Span detail) {
     r.kind = (uint8_t)kind;
     r.cause = (uint8_t)cause;
@@ -736,6 +1004,10 @@ __device__ __forceinline__ void validate_one(Req& d, int64_t n, const wsg_hs_con
       r.detail_len = (uint16_t)(detail.e - detail.b);
     }
     *res = r;
+    if constexpr (NEG) {
+      if (kind == WSG_HS_FINISHED) put_negotiated(negotiated, proto, ext);
+      else put_negotiated(negotiated, Span{-1, -1}, 0u);
+    }
   };
   const Span none{-1, -1};
   int capped = 0;
@@ -921,6 +1193,49 @@ __device__ __forceinline__ void validate_one(Req& d, int64_t n, const wsg_hs_con
   }
   // validateSubProtocol (:462-485): a match against the configured list is Java's
   const Span pr = fld[C_PROTOCOL];
+  if constexpr (NEG) {
+    // the whole value against the list ("*" is an entry like any other here)
+    if (neg.n_protocols) {
+      if (pr.b < 0) {
+        finish(WSG_HS_CLOSING, WSG_HSC_MISSING_SUBPROTOCOL, none);
+        return;
+      }
+      if (!proto_supported(d, pr, neg)) {
+        finish(WSG_HS_CLOSING, WSG_HSC_INVALID_SUBPROTOCOL, pr);
+        return;
+      }
+      proto = pr;
+    } else if (pr.b >= 0) {
+      finish(WSG_HS_CLOSING, WSG_HSC_INVALID_SUBPROTOCOL, pr);
+      return;
+    }
+    // validateExtensions (:487-533): every element must be an answer validateResponse
+    // takes, and only one of them (the group check); a throw names its text
+    const Span xf = fld[C_EXTENSIONS];
+    if (xf.b >= 0) {
+      if (neg.other_extensions) {
+        finish(WSG_HS_DEFER, WSG_HSC_D_EXTENSION, none);
+        return;
+      }
+      int cause = neg.deflate ? 0 : WSG_HSC_INVALID_EXTENSIONS;
+      if (neg.deflate)
+        each_value(d, xf, [&](Span el) {
+          uint32_t found = 0u;
+          const int v = pmd_parse(d, el, &found);
+          const uint32_t x = v == 0 ? pmd_validate_response(neg, found) : 0u;
+          if (v > 0) cause = v;
+          else if (!x || ext) cause = WSG_HSC_INVALID_EXTENSIONS;
+          ext = x;
+          return cause != 0;
+        });
+      if (cause) {
+        finish(WSG_HS_CLOSING, cause, none);
+        return;
+      }
+    }
+    finish(WSG_HS_FINISHED, WSG_HSC_NONE, none);
+    return;
+  }
   if (cfg.subprotocols) {
     if (pr.b < 0) {
       finish(WSG_HS_CLOSING, WSG_HSC_MISSING_SUBPROTOCOL, none);
@@ -956,7 +1271,26 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WSG_HS_VWAV
   d.lead = (uint32_t)(b & 15u);
   const uint32_t* kp = reinterpret_cast<const uint32_t*>(keys + (uint64_t)i * 24u);
   const KeyWords k{kp[0], kp[1], kp[2], kp[3], kp[4], kp[5]};
-  validate_one(d, (int64_t)(e - b), cfg, k, expected + (uint64_t)i * WSG_HS_EXPECTED_STRIDE, result + i);
+  validate_one<false>(d, (int64_t)(e - b), cfg, NoNeg{}, k, expected + (uint64_t)i * WSG_HS_EXPECTED_STRIDE, result + i,
+                      nullptr);
+}
+
+#ifndef WSG_HS_NEG_VWAVES
+#define WSG_HS_NEG_VWAVES WSG_HS_VWAVES
+#endif
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WSG_HS_NEG_VWAVES))) void k_hs_validate_neg(
+    wsg_hs_config cfg, HsNeg neg, const uint8_t* resp, const uint64_t* resp_off, const uint8_t* keys, uint32_t n,
+    uint8_t* expected, wsg_hs_result* result, wsg_hs_negotiated* negotiated) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const uint64_t b = resp_off[i], e = resp_off[i + 1];
+  Req d;
+  d.base = reinterpret_cast<const uint4*>(resp + (b & ~(uint64_t)15));
+  d.lead = (uint32_t)(b & 15u);
+  const uint32_t* kp = reinterpret_cast<const uint32_t*>(keys + (uint64_t)i * 24u);
+  const KeyWords k{kp[0], kp[1], kp[2], kp[3], kp[4], kp[5]};
+  validate_one<true>(d, (int64_t)(e - b), cfg, neg, k, expected + (uint64_t)i * WSG_HS_EXPECTED_STRIDE, result + i,
+                     negotiated + i);
 }
 
 }  // namespace
@@ -966,6 +1300,44 @@ void launch_hs_validate(const wsg_hs_config& cfg, const uint8_t* resp, const uin
   if (n)
     hipLaunchKernelGGL(k_hs_validate, dim3((n + 255) / 256), dim3(256), 0, s, cfg, resp, resp_off, keys, n, expected,
                        result);
+}
+
+// wsg_hs_negotiation checked and repacked for the kernels
+bool hs_neg_pack(const wsg_hs_negotiation& in, HsNeg* out) {
+  if (in.n_protocols > WSG_HS_NEG_MAX_PROTOCOLS || in.deflate > 1 || in.other_extensions > 1 ||
+      in.compress_no_context > WSG_HS_NOCONTEXT_REQUIRED || in.decompress_no_context > WSG_HS_NOCONTEXT_REQUIRED)
+    return false;
+  if (in.n_protocols && in.protocol_off[0] != 0) return false;
+  memset(out, 0, sizeof *out);
+  out->n_protocols = in.n_protocols;
+  out->deflate = in.deflate;
+  out->other_extensions = in.other_extensions;
+  out->compress_no_context = in.compress_no_context;
+  out->decompress_no_context = in.decompress_no_context;
+  for (int k = 0; k < in.n_protocols; ++k) {
+    const uint32_t b = in.protocol_off[k], e = in.protocol_off[k + 1];
+    if (e < b || e > WSG_HS_NEG_MAX_PROTOCOL_BYTES) return false;
+    out->off[k + 1] = (uint16_t)e;
+    if (e - b == 1 && in.protocol_bytes[b] == '*') out->star = 1;
+  }
+  memcpy(out->words, in.protocol_bytes, in.n_protocols ? in.protocol_off[in.n_protocols] : 0);  // little-endian host
+  return true;
+}
+
+void launch_hs_accept_neg(const wsg_hs_config& cfg, const HsNeg& neg, const uint8_t* req, const uint64_t* req_off,
+                          uint32_t n, uint8_t* resp, wsg_hs_result* result, wsg_hs_negotiated* negotiated,
+                          hipStream_t s) {
+  if (n)
+    hipLaunchKernelGGL(k_hs_accept_neg, dim3((n + 255) / 256), dim3(256), 0, s, cfg, neg, req, req_off, n, resp, result,
+                       negotiated);
+}
+
+void launch_hs_validate_neg(const wsg_hs_config& cfg, const HsNeg& neg, const uint8_t* resp, const uint64_t* resp_off,
+                            const uint8_t* keys, uint32_t n, uint8_t* expected, wsg_hs_result* result,
+                            wsg_hs_negotiated* negotiated, hipStream_t s) {
+  if (n)
+    hipLaunchKernelGGL(k_hs_validate_neg, dim3((n + 255) / 256), dim3(256), 0, s, cfg, neg, resp, resp_off, keys, n,
+                       expected, result, negotiated);
 }
 
 void launch_hs_accept(const wsg_hs_config& cfg, const uint8_t* req, const uint64_t* req_off, uint32_t n,

@@ -315,7 +315,7 @@ enum KernelId {
   K_PARSE = 0, K_SCAN, K_LINK, K_UNMASK, K_FINAL,
   K_ENC_LEN, K_ENC_SCAN, K_ENC_EMIT, K_ENC_FINAL, K_ENC_DESC, K_AGG, K_AGG_GATHER, K_INFLATE, K_HS_ACCEPT, K_INFL_TOK, K_INFL_FAST, K_HS_VALIDATE,
   K_DEFL_PLAN, K_DEFL_PREP, K_DEFL_MATCH, K_DEFL_PARSE, K_DEFL_FINAL, K_DEFL_SERIAL, K_DEFL_TREES, K_DEFL_EMIT,
-  K_DEFL_HIST, K_DEFL_MATCH_LDS, K_DEFL_LINKS, K_COUNT
+  K_DEFL_HIST, K_DEFL_MATCH_LDS, K_DEFL_LINKS, K_HS_ACCEPT_NEG, K_HS_VALIDATE_NEG, K_COUNT
 };
 
 // launchers (enqueue on `s`; the timing hook wraps each one)
@@ -409,6 +409,24 @@ void launch_hs_accept(const wsg_hs_config& cfg, const uint8_t* req, const uint64
 void launch_hs_validate(const wsg_hs_config& cfg, const uint8_t* resp, const uint64_t* resp_off, const uint8_t* keys,
                         uint32_t n, uint8_t* expected, wsg_hs_result* result, hipStream_t s);
 __host__ __device__ int hs_frame_len(const uint8_t* d, int64_t len, int* capped, int64_t* lines_end);
+
+// wsg_hs_negotiation as the negotiating kernels take it, by value (uniform across the
+// grid: its reads are scalar loads from the kernel arguments): the supported
+// subprotocols as little-endian dwords, so a byte is a shift of a scalar dword.
+struct HsNeg {
+  uint8_t n_protocols, deflate, other_extensions, compress_no_context, decompress_no_context;
+  uint8_t star;  // an entry is "*": the first requested token wins (Handshaker.java:270)
+  uint16_t off[WSG_HS_NEG_MAX_PROTOCOLS + 1];
+  uint32_t words[WSG_HS_NEG_MAX_PROTOCOL_BYTES / 4];
+};
+// false: a malformed struct (the rules in wsgpu.h)
+bool hs_neg_pack(const wsg_hs_negotiation& in, HsNeg* out);
+void launch_hs_accept_neg(const wsg_hs_config& cfg, const HsNeg& neg, const uint8_t* req, const uint64_t* req_off,
+                          uint32_t n, uint8_t* resp, wsg_hs_result* result, wsg_hs_negotiated* negotiated,
+                          hipStream_t s);
+void launch_hs_validate_neg(const wsg_hs_config& cfg, const HsNeg& neg, const uint8_t* resp, const uint64_t* resp_off,
+                            const uint8_t* keys, uint32_t n, uint8_t* expected, wsg_hs_result* result,
+                            wsg_hs_negotiated* negotiated, hipStream_t s);
 
 
 }  // namespace ws

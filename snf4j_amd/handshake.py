@@ -13,6 +13,13 @@ request: write `response` and either switch the session to the frame codec (101)
 or close it with `message` (the exception message or the Handshaker closing
 reason).  DEFER means the Java Handshaker takes the request (include/wsgpu.h lists
 the forms); NEED_MORE means the frame is not complete yet.
+
+With a `Negotiation` in the config (the supported subprotocols and the NoContext
+settings of one PerMessageDeflateExtension) both handshakers call the negotiating
+entry points (k_hs_accept_neg / k_hs_validate_neg), which decide subprotocol and
+permessage-deflate offers and answers instead of deferring them
+(Handshaker.java:259-325, 462-533; PerMessageDeflateExtension.java:177-301); the
+outcomes then carry `subprotocol` and `deflate`.
 """
 from __future__ import annotations
 
@@ -21,7 +28,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _lib
-from ._lib import HsConfig, lib
+from ._lib import HsConfig, HsNegotiation, lib
 
 NEED_MORE, DEFER, PARSE_ERROR, ACCEPT, FINISHED, CLOSING = 0, 1, 2, 3, 4, 5
 
@@ -34,13 +41,20 @@ MESSAGES = {1: "Invalid http request", 2: "Invalid http request version", 3: "Fo
             15: "Invalid http response", 16: "Invalid http response version", 17: "Invalid http response status",
             18: "Invalid websocket response status: %s", 19: "Missing websocket key challenge",
             20: "Invalid websocket key challenge. Actual: %s. Expected: %s", 21: "Missing websocket sub protocol",
-            22: "Invalid websocket sub protocol: %s"}
+            22: "Invalid websocket sub protocol: %s",
+            24: "Invalid websocket request extension", 25: "Invalid extension: Duplicated parameter",
+            26: "Invalid extension: Unnecessary parameter value", 27: "Invalid extension: Missing parameter value",
+            28: "Invalid extension: Invalid parameter value format", 29: "Invalid extension: Invalid parameter value",
+            30: "Invalid extension: Unexpected parameter"}
 CAUSE_NAMES = {0: "NONE", 1: "BAD_REQUEST_LINE", 2: "BAD_VERSION", 3: "FORBIDDEN", 4: "TOO_LARGE",
                5: "MISSING_VERSION", 6: "INCORRECT_VERSION", 7: "UNSUPPORTED_VERSION", 8: "MISSING_UPGRADE",
                9: "MISSING_CONNECTION", 10: "INVALID_UPGRADE", 11: "INVALID_CONNECTION", 12: "MISSING_HOST",
                13: "MISSING_KEY", 14: "INVALID_KEY", 15: "BAD_RESPONSE_LINE", 16: "BAD_RESPONSE_VERSION",
                17: "BAD_RESPONSE_STATUS", 18: "INVALID_STATUS", 19: "MISSING_ACCEPT", 20: "INVALID_ACCEPT",
-               21: "MISSING_SUBPROTOCOL", 22: "INVALID_SUBPROTOCOL", 23: "INVALID_EXTENSIONS", 32: "D_LINE_FORM", 33: "D_REPEATED", 34: "D_NON_ASCII",
+               21: "MISSING_SUBPROTOCOL", 22: "INVALID_SUBPROTOCOL", 23: "INVALID_EXTENSIONS",
+               24: "INVALID_REQUEST_EXTENSION", 25: "EXT_DUPLICATED", 26: "EXT_UNNECESSARY_VALUE",
+               27: "EXT_MISSING_VALUE", 28: "EXT_VALUE_FORMAT", 29: "EXT_VALUE", 30: "EXT_UNEXPECTED",
+               32: "D_LINE_FORM", 33: "D_REPEATED", 34: "D_NON_ASCII",
                35: "D_URI", 36: "D_HOST", 37: "D_SUBPROTOCOL", 38: "D_EXTENSION", 39: "D_POLICY", 40: "D_LINES"}
 KIND_NAMES = {NEED_MORE: "need_more", DEFER: "defer", PARSE_ERROR: "parse_error", ACCEPT: "accept",
               FINISHED: "finished", CLOSING: "closing"}
@@ -55,6 +69,64 @@ def available(data: bytes) -> int:
     return r
 
 
+FORBIDDEN, OPTIONAL, REQUIRED = 0, 1, 2   # PerMessageDeflateExtension.NoContext
+
+
+@dataclass(frozen=True)
+class DeflateNegotiation:
+    """The PerMessageDeflateExtension of getSupportedExtensions(): its two NoContext
+    settings (PerMessageDeflateExtension.java:60-112; the fields are private there, so
+    they are given here)."""
+    compress_no_context: int = OPTIONAL
+    decompress_no_context: int = OPTIONAL
+
+
+@dataclass(frozen=True)
+class Negotiation:
+    """What the negotiating entry points decide on the device (wsg_hs_negotiation):
+    getSupportedSubProtocols() and a getSupportedExtensions() of one
+    PerMessageDeflateExtension.  other_extensions: the list holds anything else, and an
+    extensions field is deferred as before."""
+    subprotocols: tuple = ()
+    deflate: DeflateNegotiation | None = None
+    other_extensions: bool = False
+
+    def native(self) -> HsNegotiation | None:
+        """The ABI struct, or None when the lists exceed its caps (16 entries, 256 bytes,
+        ASCII): the caller then sets the old flags, and offers are deferred."""
+        try:
+            protos = [p.encode("ascii") for p in self.subprotocols]
+        except UnicodeEncodeError:
+            return None
+        if len(protos) > _lib.HS_NEG_MAX_PROTOCOLS or sum(map(len, protos)) > _lib.HS_NEG_MAX_PROTOCOL_BYTES:
+            return None
+        g = HsNegotiation()
+        g.n_protocols = len(protos)
+        g.deflate = int(self.deflate is not None)
+        g.other_extensions = int(self.other_extensions)
+        if self.deflate is not None:
+            g.compress_no_context = int(self.deflate.compress_no_context)
+            g.decompress_no_context = int(self.deflate.decompress_no_context)
+        blob, at = b"".join(protos), 0
+        for k, p in enumerate(protos):
+            at += len(p)
+            g.protocol_off[k + 1] = at
+        g.protocol_bytes[:len(blob)] = blob
+        return g
+
+
+def _negotiated(data: bytes, ng, server: bool):
+    """(subprotocol, deflate) of a wsg_hs_negotiated record: deflate is None or
+    (encoder_no_context, decoder_no_context) for this side
+    (PerMessageDeflateExtension.updateEncoders / updateDecoders, :307-327)."""
+    n, ext = int(ng["proto_len"]), int(ng["ext"])
+    proto = data[int(ng["proto_off"]):int(ng["proto_off"]) + n].decode("ascii") if n else None
+    if not ext & _lib.HS_EXT_DEFLATE:
+        return proto, None
+    cnc, snc = bool(ext & _lib.HS_EXT_CLIENT_NO_CONTEXT), bool(ext & _lib.HS_EXT_SERVER_NO_CONTEXT)
+    return proto, ((snc, cnc) if server else (cnc, snc))
+
+
 @dataclass
 class HandshakeConfig:
     """The IWebSocketSessionConfig values the server handshake reads
@@ -64,10 +136,15 @@ class HandshakeConfig:
     supported_subprotocols: bool = False   # getSupportedSubProtocols() != null
     supported_extensions: bool = False     # getSupportedExtensions() != null
     custom_policy: bool = False            # acceptRequestUri / customizeHeaders overridden
+    negotiation: Negotiation | None = None  # the lists themselves: offers are decided on the device
 
     def native(self) -> HsConfig:
+        sub, ext = self.supported_subprotocols, self.supported_extensions
+        if self.negotiation is not None:  # (read only when the lists exceed the ABI caps)
+            sub = bool(self.negotiation.subprotocols)
+            ext = self.negotiation.deflate is not None or self.negotiation.other_extensions
         return HsConfig(self.max_handshake_frame_length, int(self.ignore_host_header_field),
-                        int(self.supported_subprotocols), int(self.supported_extensions), int(self.custom_policy))
+                        int(sub), int(ext), int(self.custom_policy))
 
 
 @dataclass
@@ -78,6 +155,8 @@ class HandshakeOutcome:
     frame_len: int
     response: bytes
     message: str | None
+    subprotocol: str | None = None   # Handshaker.getSubProtocol()
+    deflate: tuple | None = None     # permessage-deflate accepted: (encoder_no_context, decoder_no_context)
 
     @property
     def switched(self) -> bool:
@@ -99,8 +178,15 @@ class BatchHandshaker:
         off = np.zeros(len(reqs) + 1, dtype=np.uint64)
         off[1:] = np.cumsum([len(r) for r in reqs]) if reqs else []
         buf = np.frombuffer(b"".join(reqs), dtype=np.uint8)
-        resp, res = self.ctx.handshake_accept_host(self.config.native(), buf, off)
-        return [self._outcome(reqs[i], resp[i], res[i]) for i in range(len(reqs))]
+        neg = self.config.negotiation.native() if self.config.negotiation is not None else None
+        if neg is None:
+            resp, res = self.ctx.handshake_accept_host(self.config.native(), buf, off)
+            return [self._outcome(reqs[i], resp[i], res[i]) for i in range(len(reqs))]
+        resp, res, ng = self.ctx.handshake_accept_negotiate_host(self.config.native(), neg, buf, off)
+        outs = [self._outcome(reqs[i], resp[i], res[i]) for i in range(len(reqs))]
+        for i, o in enumerate(outs):
+            o.subprotocol, o.deflate = _negotiated(reqs[i], ng[i], True)
+        return outs
 
     @staticmethod
     def _outcome(req: bytes, resp, r) -> HandshakeOutcome:
@@ -153,10 +239,14 @@ class ClientConfig:
     max_handshake_frame_length: int = 65536
     supported_subprotocols: tuple = ()      # getSupportedSubProtocols()
     supported_extensions: bool = False      # getSupportedExtensions() non-empty
+    negotiation: Negotiation | None = None  # the lists themselves: answers are decided on the device
 
     def native(self) -> HsConfig:
-        return HsConfig(self.max_handshake_frame_length, 0, int(bool(self.supported_subprotocols)),
-                        int(self.supported_extensions), 0)
+        sub, ext = bool(self.supported_subprotocols), self.supported_extensions
+        if self.negotiation is not None:  # (read only when the lists exceed the ABI caps)
+            sub = bool(self.negotiation.subprotocols)
+            ext = self.negotiation.deflate is not None or self.negotiation.other_extensions
+        return HsConfig(self.max_handshake_frame_length, 0, int(sub), int(ext), 0)
 
 
 @dataclass
@@ -167,6 +257,8 @@ class ClientHandshakeOutcome:
     frame_len: int
     expected: str | None      # generateAnswerKey(key), once the frame is complete
     message: str | None       # the exception message (PARSE_ERROR) or getClosingReason() (CLOSING)
+    subprotocol: str | None = None   # Handshaker.getSubProtocol()
+    deflate: tuple | None = None     # permessage-deflate validated: (encoder_no_context, decoder_no_context)
 
     @property
     def finished(self) -> bool:
@@ -191,8 +283,15 @@ class BatchClientHandshaker:
         off[1:] = np.cumsum([len(r) for r in rs]) if rs else []
         buf = np.frombuffer(b"".join(rs), dtype=np.uint8)
         kb = np.frombuffer(b"".join(ks), dtype=np.uint8)
-        exp, res = self.ctx.handshake_validate_host(self.config.native(), buf, off, kb)
-        return [self._outcome(rs[i], exp[i], res[i]) for i in range(len(rs))]
+        neg = self.config.negotiation.native() if self.config.negotiation is not None else None
+        if neg is None:
+            exp, res = self.ctx.handshake_validate_host(self.config.native(), buf, off, kb)
+            return [self._outcome(rs[i], exp[i], res[i]) for i in range(len(rs))]
+        exp, res, ng = self.ctx.handshake_validate_negotiate_host(self.config.native(), neg, buf, off, kb)
+        outs = [self._outcome(rs[i], exp[i], res[i]) for i in range(len(rs))]
+        for i, o in enumerate(outs):
+            o.subprotocol, o.deflate = _negotiated(rs[i], ng[i], False)
+        return outs
 
     @staticmethod
     def _outcome(resp: bytes, exp, r) -> ClientHandshakeOutcome:
